@@ -15,8 +15,16 @@ scaling  N = 1: BASELINE configs[1].  N > 1: the headline line is BASELINE confi
 GPU); under `torch.distributed.run` (RANK / WORLD_SIZE set) it is one of the ranks.
 
 One JSON line on stdout (rank 0).  `roofline` is measured with HIP events on the stream the kernels run on, inside
-the timed region; `cpu_baseline` is the CPU port of the reference algorithm (Julia is not installed, so not the
-reference itself) timed on a bounded sample on rank 0 at N == 1.
+the timed region.
+
+A plain run measures the headline alone: set-up, the untimed pre-heat and W warm-up steps, the K timed steps, the
+result line.  `--full` adds everything else the benchmark measures and checks: the cold-start steps, the library's
+default mode, the per-stage kernel times (`kernel_ms_per_step`, `pass_hbm`), the side legs (dense tensor, record
+consumers, host entry, configs[3] / configs[4] shard shapes), the train step, and `cpu_baseline` - the CPU port of the
+reference algorithm (Julia is not installed, so not the reference itself) timed on a bounded sample on rank 0 at N == 1.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's shard; see dump_outputs) as .npy
+files; the inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -58,7 +66,36 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="only the timed scan (+ train): skip dense / consumers / host-entry legs")
     ap.add_argument("--no-big", action="store_true", help="skip the configs[3] / configs[4] shard-shape legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: cold start, default mode, per-stage kernel times, side legs, train step, CPU baselines "
+                         "(--no-train / --no-cpu / --no-extras / --no-big trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 20   # records per strand written by --dump-outputs: 24 B each (3 + 1 float32 columns, a float64 index), 48 MB in all
+DUMP_SEED = 20261016
+
+
+def dump_outputs(path, sh, totals):
+    """What one step of the timed path hands its caller (pwm_scan_hits_both_dev with a histogram): per strand the totals, the
+    hit records (m, n, l) and their binary16 scores, and the 2 x K per-PWM hit counts.  The records (57 M per step at
+    configs[1]) go as a fixed, seeded sample of row indices per strand, the same for every build that finds the same number
+    of hits; `*_rows` holds the indices.  Every value is exact in the float type it is written in."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    out = {"hit_totals": np.asarray(totals, dtype=np.float64),
+           "hit_counts": sh["counts"].cpu().numpy().astype(np.float64)}
+    for rc, tag in enumerate(("fwd", "rev")):
+        n = int(totals[rc])
+        rows = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.default_rng(DUMP_SEED + rc).integers(0, n, DUMP_SAMPLE))
+        rows_t = torch.from_numpy(rows).to(sh["hits"][rc].device)
+        out[f"hits_{tag}"] = sh["hits"][rc].index_select(0, rows_t).cpu().numpy().astype(np.float32)
+        out[f"scores_{tag}"] = sh["hsc"][rc].index_select(0, rows_t).cpu().numpy().view(np.float16).astype(np.float32)
+        out[f"hits_{tag}_rows"] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -106,6 +143,8 @@ def timed_region(step, steps, sync, barrier):
 
 def main():
     args = parse()
+    if not args.full:       # a plain run is the headline alone: every side leg below is --full's
+        args.no_train = args.no_cpu = args.no_extras = args.no_big = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
 
@@ -198,11 +237,11 @@ def main():
                 "ptrs": (dcodes.data_ptr(), [h.data_ptr() for h in hits], [s.data_ptr() for s in hsc], counts.data_ptr())}
 
     def scan_step(sh):
-        tot = 0
+        tot = (0, 0)
         if sh["n"]:
             # gpu_scan (_h3_1_alignment.jl:89-99): forward and reverse strand in one call, one host wait
             pc, ph, ps, pk = sh["ptrs"]
-            tot = sum(ctx.pwm_scan_hits_both_dev(bank, lens, pc, sh["n"], L, ph, ps, sh["cap"], n0=sh["n0"], counts_ptr=pk))
+            tot = ctx.pwm_scan_hits_both_dev(bank, lens, pc, sh["n"], L, ph, ps, sh["cap"], n0=sh["n0"], counts_ptr=pk)
         if world > 1:   # the one real exchange of the scan: the K int64 hit counts of both strands, queued on the
             reducer.hist_sum_(sh["counts"])  # scan's stream behind the kernels that wrote them (motifs_hist_allreduce); the next scan queues behind it
         return tot
@@ -215,15 +254,16 @@ def main():
     # five steps after an idle spell).  A fixed untimed pre-heat precedes the W warm-up steps so that the K timed steps
     # measure the steady state whatever W is.
     PREHEAT = 150      # (round 5: 40 left the first timed region ~2 % slower than the second whichever mode came first; steps 40-150 still speed up)
-    # ... and the other clock, for the record: the first five steps after the set-up and half a second of idling, each
-    # waited for on its own (what a caller who scans once sees)
-    time.sleep(0.5)
+    # ... and the other clock, for the record (--full): the first five steps after the set-up and half a second of idling,
+    # each waited for on its own (what a caller who scans once sees)
     cold = []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        scan_step(weak)
-        sync()
-        cold.append((time.perf_counter() - t0) * 1e3)
+    if args.full:
+        time.sleep(0.5)
+        for _ in range(5):
+            t0 = time.perf_counter()
+            scan_step(weak)
+            sync()
+            cold.append((time.perf_counter() - t0) * 1e3)
     for _ in range(PREHEAT):
         scan_step(weak)
     for _ in range(args.warmup):
@@ -233,8 +273,11 @@ def main():
     # microseconds of stream time per section; the other kernels are timed in an extra pass after the clock has stopped
     ctx.enable_timing(slots=[lib.KS_SCAN_COUNT])
     ctx.reset_timing()
-    dt, nhits = timed_region(lambda: scan_step(weak), args.steps, sync, barrier)
+    dt, last_tot = timed_region(lambda: scan_step(weak), args.steps, sync, barrier)
     ctx.enable_timing(False)
+    nhits = sum(last_tot)
+    if args.dump_outputs and world == 1:     # (N > 1: the headline is the strong split, dumped below)
+        dump_outputs(args.dump_outputs, weak, last_tot)
     if world > 1:
         dt = float(par.host_all_reduce(torch.tensor([dt], dtype=torch.float64), dist.ReduceOp.MAX).item())
     tot_hits = torch.tensor([nhits], dtype=torch.int64)
@@ -242,25 +285,26 @@ def main():
         par.HostReducer(ctx).sum_i64_(tot_hits)
 
     kms = {"count": ctx.kernel_ms(lib.KS_SCAN_COUNT)}
-    # the library's DEFAULT mode for the same K steps (every call waits for its records, as all rounds before the fourth measured it)
-    ctx.set_records_in_stream_order(False)
-    for _ in range(args.warmup):
-        scan_step(weak)
-    ctx.enable_timing(slots=[lib.KS_SCAN_COUNT])        # the same event pair per step as in the headline region
-    dt_default, _ = timed_region(lambda: scan_step(weak), args.steps, sync, barrier)
-    ctx.enable_timing(False)
-    ctx.reset_timing()
-    if world > 1:
-        dt_default = float(par.host_all_reduce(torch.tensor([dt_default], dtype=torch.float64), dist.ReduceOp.MAX).item())
-    ctx.set_records_in_stream_order(True)
-    ctx.enable_timing(slots=[lib.KS_SCAN_OFFSETS, lib.KS_SCAN_FILL])
-    ctx.reset_timing()
-    for _ in range(args.steps):
-        scan_step(weak)
-    sync()
-    ctx.enable_timing(False)
-    kms["offsets"] = ctx.kernel_ms(lib.KS_SCAN_OFFSETS)
-    kms["fill"] = ctx.kernel_ms(lib.KS_SCAN_FILL)
+    if args.full:
+        # the library's DEFAULT mode for the same K steps (every call waits for its records, as all rounds before the fourth measured it)
+        ctx.set_records_in_stream_order(False)
+        for _ in range(args.warmup):
+            scan_step(weak)
+        ctx.enable_timing(slots=[lib.KS_SCAN_COUNT])        # the same event pair per step as in the headline region
+        dt_default, _ = timed_region(lambda: scan_step(weak), args.steps, sync, barrier)
+        ctx.enable_timing(False)
+        ctx.reset_timing()
+        if world > 1:
+            dt_default = float(par.host_all_reduce(torch.tensor([dt_default], dtype=torch.float64), dist.ReduceOp.MAX).item())
+        ctx.set_records_in_stream_order(True)
+        ctx.enable_timing(slots=[lib.KS_SCAN_OFFSETS, lib.KS_SCAN_FILL])
+        ctx.reset_timing()
+        for _ in range(args.steps):
+            scan_step(weak)
+        sync()
+        ctx.enable_timing(False)
+        kms["offsets"] = ctx.kernel_ms(lib.KS_SCAN_OFFSETS)
+        kms["fill"] = ctx.kernel_ms(lib.KS_SCAN_FILL)
 
     # ---- strong scaling: BASELINE configs[2] as written (the same N reads split over the ranks) -------------------
     strong = None
@@ -268,7 +312,7 @@ def main():
     if world > 1:
         all_codes = sy.gen_codes(N, L, seed, n_plant=5, k=PL)          # the rank-0 shard of the weak run, on every rank
         modes = {}
-        for mode, align in (("ordering_batches", lib.SCAN_BATCH), ("even", 1)):
+        for mode, align in (("ordering_batches", lib.SCAN_BATCH), ("even", 1)) if args.full else (("even", 1),):
             lo, hi = par.shard_range(N, rank, world, align=align)
             sh = make_shard(np.ascontiguousarray(all_codes[lo:hi]), lo)
             for _ in range(PREHEAT + args.warmup):
@@ -277,10 +321,12 @@ def main():
             if mode == "even":
                 ctx.enable_timing(slots=[lib.KS_SCAN_COUNT])
                 ctx.reset_timing()
-            sdt, sh_hits = timed_region(lambda: scan_step(sh), args.steps, sync, barrier)
+            sdt, sh_tot = timed_region(lambda: scan_step(sh), args.steps, sync, barrier)
             if mode == "even":
                 ctx.enable_timing(False)
                 strong_kms = ctx.kernel_ms(lib.KS_SCAN_COUNT)
+                if args.dump_outputs and rank == 0:
+                    dump_outputs(args.dump_outputs, sh, sh_tot)
             sdt = float(par.host_all_reduce(torch.tensor([sdt], dtype=torch.float64), dist.ReduceOp.MAX).item())
             sizes = [b - a for a, b in (par.shard_range(N, r, world, align=align) for r in range(world))]
             modes[mode] = {"value": float(N) * L * args.steps / sdt, "unit": "bases/s", "ms_per_step": sdt / args.steps * 1e3,
@@ -810,9 +856,6 @@ def main():
         n_launch = max(strong_kms[1], 1)
         strands_per_launch = 2.0 * args.steps / n_launch
         cand_ms = strong_kms[0] / n_launch
-    pass_ms = (kms["count"][0] + kms["offsets"][0] + kms["fill"][0]) / (2.0 * args.steps)    # one strand's share of a step's kernels
-    alg_bytes = N * L + hits_per_pass * 14 + K * 8
-    pass_gbs = alg_bytes / (pass_ms * 1e-3) / 1e9
     cand_flops = 2.0 * 4 * PL * K * float(head_reads) * Lout * strands_per_launch
     cand_tflops = cand_flops / (cand_ms * 1e-3) / 1e12
     traffic, traffic_src = None, None
@@ -835,12 +878,17 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": strong["ms_per_step"] if world > 1 else dt / args.steps * 1e3,
-        "ms_per_step_default_mode": dt_default / args.steps * 1e3,
-        "ms_per_step_default_mode_note": "the same shard and step count with motifs_ctx_set_records_in_stream_order off (the library default: every call returns "
-                                         "with its records written); `ms_per_step` / `value` are measured with it on (config.records_in_stream_order); at N > 1 this "
-                                         "is the weak-scaling shard, not the configs[2] split",
-        "cold_start_ms_per_step": sum(cold) / len(cold),
-        "cold_start_ms_each": cold,
+    }
+    if args.full:
+        out.update({
+            "ms_per_step_default_mode": dt_default / args.steps * 1e3,
+            "ms_per_step_default_mode_note": "the same shard and step count with motifs_ctx_set_records_in_stream_order off (the library default: every call returns "
+                                             "with its records written); `ms_per_step` / `value` are measured with it on (config.records_in_stream_order); at N > 1 this "
+                                             "is the weak-scaling shard, not the configs[2] split",
+            "cold_start_ms_per_step": sum(cold) / len(cold),
+            "cold_start_ms_each": cold,
+        })
+    out.update({
         "higher_is_better": True,
         "scaling": "strong" if world > 1 else "weak",
         "vs_baseline": None,
@@ -874,18 +922,23 @@ def main():
             "note": "per tile of a wave: 12 matrix instructions (384 cycles of the matrix pipe) and 86 vector instructions (one v_alignbit per sign "
                     "bit) on the same issue port, ISA count in DESIGN 2.7-2 - the two are level, which caps this fraction near 0.6",
         },
-        "pass_hbm": {
+    })
+    if args.full:
+        pass_ms = (kms["count"][0] + kms["offsets"][0] + kms["fill"][0]) / (2.0 * args.steps)    # one strand's share of a step's kernels
+        alg_bytes = N * L + hits_per_pass * 14 + K * 8
+        pass_gbs = alg_bytes / (pass_ms * 1e-3) / 1e9
+        out["pass_hbm"] = {
             "kernels": "scan_cand_kernel + stage_hits + row scan + emit_records (one strand pass)",
             "bound": "hbm", "achieved": pass_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": pass_gbs / HBM_PEAK_GBS,
             "algorithmic_bytes": alg_bytes, "avg_pass_ms": pass_ms,
             "note": "fused-hits contract (N*L codes in, 14 B per hit out, no dense score tensor): the pass is bound "
                     "by the matrix cores and the exact re-scoring, not by HBM; dense_kernel is the a17 dense-score contract",
-        },
-        "strong": strong,
-        "weak": weak_line,
-        "kernel_ms_per_step": {"scan_cand": kms["count"][0] / args.steps, "stage_hits_row_scan": kms["offsets"][0] / args.steps,
-                               "emit_records": kms["fill"][0] / args.steps},
-    }
+        }
+    out["strong"] = strong
+    out["weak"] = weak_line
+    if args.full:
+        out["kernel_ms_per_step"] = {"scan_cand": kms["count"][0] / args.steps, "stage_hits_row_scan": kms["offsets"][0] / args.steps,
+                                     "emit_records": kms["fill"][0] / args.steps}
     out.update(extras)
     if train is not None:
         out["train"] = train
@@ -988,8 +1041,9 @@ def main():
         out["code_retrieval_reads_per_s"] = tr["code_retrieval"]["reads_per_s"]
     if "dense_kernel" in out:
         out["dense_frac"] = out["dense_kernel"]["frac"]
-    out["cfg3_shard_ms"] = out.get("cfg3_shard", {}).get("ms_per_step_both_strands")
-    out["cfg4_shard_ms"] = out.get("cfg4_shard", {}).get("ms_per_step_both_strands")
+    if args.full:
+        out["cfg3_shard_ms"] = out.get("cfg3_shard", {}).get("ms_per_step_both_strands")
+        out["cfg4_shard_ms"] = out.get("cfg4_shard", {}).get("ms_per_step_both_strands")
     out["ms_per_step_again"] = out["ms_per_step"]
     print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 """Per-launch-shape kernel durations from a rocprofv3 kernel trace: the same kernel runs at several sizes inside
 bench.py (100k-read scan launches, 20k-read dense launches), which the --stats average mixes.
-usage: python tools/summarize_trace.py gpurun_out/<tag>_stats/out_kernel_trace.csv profiles/<name>.json"""
+usage: python tools/summarize_trace.py tool_out/<tag>_stats/out_kernel_trace.csv profiles/<name>.json"""
 import collections
 import csv
 import json
@@ -20,6 +20,6 @@ rows = [{"kernel": k[0], "blocks": [k[1], k[2], k[3]], "threads": k[4], "calls":
          "min_us": min(v), "max_us": max(v), "total_ms": sum(v) / 1e3} for k, v in acc.items()]
 rows.sort(key=lambda r: -r["total_ms"])
 json.dump({"source": src, "note": "durations by (kernel, launch shape); rocprofv3 --kernel-trace of bench.py --steps 5 --warmup 1 "
-           "--no-cpu --train-steps 2", "rows": rows}, open(out, "w"), indent=1)
+           "--full --no-cpu --train-steps 2", "rows": rows}, open(out, "w"), indent=1)
 for r in rows[:12]:
     print("%-34s blocks %-18s calls %4d avg %8.1f us" % (r["kernel"][:34], r["blocks"], r["calls"], r["avg_us"]))

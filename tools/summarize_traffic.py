@@ -16,7 +16,7 @@ tag, out = sys.argv[1], sys.argv[2]
 commit = sys.argv[3] if len(sys.argv) > 3 else None
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
-    with open(f"gpurun_out/{tag}_pmc_{ctr}/out_counter_collection.csv") as fh:
+    with open(f"tool_out/{tag}_pmc_{ctr}/out_counter_collection.csv") as fh:
         for r in csv.DictReader(fh):
             if r["Counter_Name"] == ctr and "motifs::" in r["Kernel_Name"]:
                 name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("motifs::", "")

@@ -2,7 +2,7 @@
 into profiles/<tag>_train_kernels_pmc.{txt,json}: per (kernel, grid) the launches of the step, the time (kernel trace of the FETCH
 pass), HBM bytes (2 x FETCH_SIZE + WRITE_SIZE KB: the gfx950 read-side correction of MI355X_MICROARCH.md), the share of wave cycles
 spent waiting and the matrix-pipe busy share, plus the step's totals (`step_hbm`).
-usage: python tools/summarize_train_pmc.py <tag> [commit]      (reads gpurun_out/<tag>_train_{FETCH_SIZE,WRITE_SIZE,sq1,sq2})"""
+usage: python tools/summarize_train_pmc.py <tag> [commit]      (reads tool_out/<tag>_train_{FETCH_SIZE,WRITE_SIZE,sq1,sq2})"""
 import collections
 import csv
 import json
@@ -14,14 +14,14 @@ commit = sys.argv[2] if len(sys.argv) > 2 else None
 
 def load(d):
     acc = collections.defaultdict(list)
-    for r in csv.DictReader(open(f"gpurun_out/{tag}_train_{d}/out_counter_collection.csv")):
+    for r in csv.DictReader(open(f"tool_out/{tag}_train_{d}/out_counter_collection.csv")):
         name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("motifs::", "")
         acc[(name, int(r["Grid_Size"]) // int(r["Workgroup_Size"]), r["Counter_Name"])].append(float(r["Counter_Value"]))
     return acc
 
 
 dur = collections.defaultdict(list)
-for r in csv.DictReader(open(f"gpurun_out/{tag}_train_FETCH_SIZE/out_kernel_trace.csv")):
+for r in csv.DictReader(open(f"tool_out/{tag}_train_FETCH_SIZE/out_kernel_trace.csv")):
     name = r["Kernel_Name"].split("(")[0].replace("void ", "").replace("motifs::", "")
     blocks = 1
     for ax in "XYZ":
