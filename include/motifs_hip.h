@@ -114,8 +114,11 @@ enum motifs_kernel_slot {
     MOTIFS_KS_SCAN_OFFSETS = 3, /* fill_row_sums + fill_row_scan: record offsets                   */
     MOTIFS_KS_SCAN_FILL = 4,    /* fill_records: (m, n, l) + fp16 score per set mask bit           */
     MOTIFS_KS_TRAIN_STEP = 5,   /* the whole forward/backward graph of motifs_model_loss_grad_dev  */
-    MOTIFS_KS_TRAIN_ISTA_BWD = 6 /* k_zy_step2_bwd, the VJP of update_ZY's fused ISTA step (model.jl:237-245): the largest kernel
+    MOTIFS_KS_TRAIN_ISTA_BWD = 6, /* k_zy_step2_bwd, the VJP of update_ZY's fused ISTA step (model.jl:237-245): the largest kernel
                                   * by time of a many-mini-batch step; stamped only on steps that run outside a captured graph */
+    MOTIFS_KS_OCC_RECORDS = 7,  /* motifs_hits_occupancy_dev: bitmap clears + the record pass (start bits, largest start per row) */
+    MOTIFS_KS_OCC_ROWS = 8,     /*   ... the row pass (union_ranges quirk, unique starts, coverage bitmaps, occupied counts)     */
+    MOTIFS_KS_OCC_OVERLAP = 9   /*   ... the pair popcounts + the mirror into the K x K output                                   */
 };
 /* on = 0: off; 1: every slot; otherwise a set of slots, (1 << (slot + 1)) or-ed together (an event pair costs a few
  * microseconds of stream time per timed section: time only what is being reported). */
@@ -389,6 +392,27 @@ int motifs_hits_filter_dev(motifs_ctx* ctx, const motifs_hit* hits_dev, const ui
  * reverse complement (submat_comlement, _3_make_pfms.jl:49-52).  codes_dev row 0 is global sequence n0 + 1. */
 int motifs_hits_count_matrices_dev(motifs_ctx* ctx, const motifs_hit* hits_dev, int64_t n, const uint8_t* codes_dev, int L,
                                    int64_t n0, const int64_t* lens, int K, int maxlen, int comp, uint32_t* counts_dev);
+
+/* get_union_ranges + total_active_position (_h4_overlap_ratio.jl:39-71), get_uniq_pos counts (:1-15) and the pair
+ * sums of get_overlap_ratio (:86-117) over up to two record arrays (forward, reverse; both pooled per read as
+ * ms.positions pools them; n_b may be 0).  Rows are motif_map[m-1] (host, K_in entries; -1 = ignore the motif's
+ * records; NULL = identity with K_out == K_in; no two motifs on one row); lens (host) are indexed by the record's m.
+ * Outputs are ADDED to (the caller zeroes them), so calls over disjoint sets of reads (chunks, shards) sum; every
+ * record of one (motif, read) must be in the same call.  uniq_dev / overlap_dev (K_out x K_out, symmetric,
+ * diagonal = occupied) may be NULL.  Records in any order.  MOTIFS_ERR_INVALID if a used record's window leaves
+ * 1..L or its read leaves n0+1..n0+N (or its m leaves 1..K_in); the outputs are then unspecified.
+ *   occupied[r] = sum over reads of the positions covered by the motif's windows, the window with the largest start
+ *                 left out when that start occurs once and another start exists (union_ranges, :48-56, keeps that quirk);
+ *   uniq[r]     = sum over reads of the distinct starts;  overlap[r][s] = sum over reads of |covered_r & covered_s|.
+ * Exact integers: the reference's Float32 pair sum equals Float32(overlap) whenever overlap < 2^24 (above that its own
+ * sum depends on the Dict iteration order).  Reads are processed in chunks of Nc = floor(limit / (4 (K_out + K16 W)))
+ * reads (at least 1), limit = motifs_ctx_set_workspace_limit's bound, W = ceil(L / 32), K16 = K_out rounded up to a
+ * multiple of 16 (K_out itself when overlap_dev is NULL); the outputs do not depend on it.  Returns after the stream
+ * has drained (the range check is read back). */
+int motifs_hits_occupancy_dev(motifs_ctx* ctx, const motifs_hit* hits_a_dev, int64_t n_a, const motifs_hit* hits_b_dev,
+                              int64_t n_b, int64_t n0, int64_t N, int L, const int64_t* lens, int K_in,
+                              const int32_t* motif_map, int K_out, int64_t* occupied_dev, int64_t* uniq_dev,
+                              int64_t* overlap_dev);
 
 /* ---- consumers of the code records (src/inference/_2_enumerate.jl) --------------------- */
 

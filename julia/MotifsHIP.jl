@@ -474,6 +474,68 @@ function hits_count_matrices!(counts::DeviceBuffer, reads::DeviceReads, hits::De
     counts
 end
 
+# get_union_ranges + total_active_position (_h4_overlap_ratio.jl:39-71), the get_uniq_pos counts (:1-15) and get_overlap_ratio's pair
+# sums (:86-117) of up to two device record arrays (forward, reverse: pooled per read as ms.positions pools them).  occupied / uniq
+# (K_out Int64) and overlap (K_out x K_out Int64, diagonal = occupied) are ADDED to: calls over disjoint reads (chunks, shards) sum.
+# motif_map[m] = output row (0-based, -1 = leave the motif out): a length window of merge_to_remove_redundancy! without compacting.
+function hits_occupancy!(occupied::DeviceBuffer, uniq::Union{DeviceBuffer, Nothing}, overlap::Union{DeviceBuffer, Nothing}, ctx::Context,
+                         hits_a::DeviceBuffer, n_a::Integer, hits_b::Union{DeviceBuffer, Nothing}, n_b::Integer, n0::Integer, N::Integer,
+                         L::Integer, lens::Vector{Int64}; K_out::Integer=length(lens), motif_map::Union{Vector{Int32}, Nothing}=nothing)
+    mm = motif_map === nothing ? Int32[] : motif_map
+    GC.@preserve lens mm check(ccall((:motifs_hits_occupancy_dev, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64, Int64, Cint, Ptr{Int64}, Cint, Ptr{Int32}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        ctx.h, hits_a.p, n_a, hits_b === nothing ? C_NULL : hits_b.p, n_b, n0, N, L, lens, length(lens),
+        motif_map === nothing ? Ptr{Int32}(C_NULL) : pointer(mm), K_out, occupied.p, uniq === nothing ? C_NULL : uniq.p,
+        overlap === nothing ? C_NULL : overlap.p))
+    nothing
+end
+# Dicts of ms.positions -> (occupied, uniq, overlap or nothing) through one call: the Dicts become one record array (they already
+# pool both strands); L defaults to the largest l + len - 1 in them
+function dict_occupancy(positions, lens; L::Union{Integer, Nothing}=nothing, overlap::Bool=true, ctx::Context=context())
+    lens = Vector{Int64}(lens); K = length(lens)
+    recs = record_t[]
+    for (i, d) in enumerate(positions), (n, ls) in d, l in ls
+        push!(recs, (UInt32(i), UInt32(n), UInt32(l)))
+    end
+    N = isempty(recs) ? 0 : Int(maximum(r[2] for r in recs))
+    Lr = isempty(recs) ? 1 : maximum(Int(r[3]) + lens[r[1]] - 1 for r in recs)
+    L = L === nothing ? Lr : max(Int(L), Lr)
+    hits = device_array(ctx, isempty(recs) ? [(UInt32(0), UInt32(0), UInt32(0))] : recs)
+    occ = DeviceBuffer(ctx, 8K); uq = DeviceBuffer(ctx, 8K); memset!(occ); memset!(uq)
+    ov = overlap ? DeviceBuffer(ctx, 8K * K) : nothing
+    overlap && memset!(ov)
+    hits_occupancy!(occ, uq, ov, ctx, hits, length(recs), nothing, 0, 0, N, L, lens)
+    a = download!(Vector{Int64}(undef, K), occ); u = download!(Vector{Int64}(undef, K), uq)
+    o = overlap ? download!(Matrix{Int64}(undef, K, K), ov) : nothing
+    free!(hits); free!(occ); free!(uq); overlap && free!(ov)
+    a, u, o
+end
+# get_overlap_ratio(ms) (_h4:86-117): Float32 of the exact pair sum, Float32(a_i + a_j) - o, zero diagonal, NaN for 0/0
+function get_overlap_ratio(ms; ctx::Context=context())
+    a, _, o = dict_occupancy(ms.positions, ms.lens; ctx=ctx)
+    K = length(a); r = zeros(Float32, K, K)
+    for j in 1:K, i in 1:K
+        i == j && continue
+        oij = Float32(o[i, j]); r[i, j] = oij / (Float32(a[i] + a[j]) - oij)
+    end
+    r
+end
+# get_fisher_p_values(ms, data; test) (_h7_fisher.jl:38-44): the occupied totals on the device; the 2x2 test stays the reference's own
+# fisher_pvec (_h7:21-36, HypothesisTests), which the caller hands over once: MotifsHIP.fisher_test[] = fisher_pvec
+const fisher_test = Ref{Any}(nothing)
+function get_fisher_p_values(ms, data; test=false, ctx::Context=context())
+    fisher_test[] === nothing && error("set MotifsHIP.fisher_test[] = fisher_pvec (src/inference/_h7_fisher.jl) first")
+    a, _, _ = dict_occupancy(ms.positions, ms.lens; L=data.L, overlap=false, ctx=ctx)
+    b, _, _ = dict_occupancy(ms.positions_bg, ms.lens; L=data.L, overlap=false, ctx=ctx)
+    fisher_test[](a, b, data; test=test)
+end
+# get_uniq_counts(ms) (_h4:13-15)
+function get_uniq_counts(ms; ctx::Context=context())
+    _, u, _ = dict_occupancy(ms.positions, ms.lens; overlap=false, ctx=ctx)
+    _, ub, _ = dict_occupancy(ms.positions_bg, ms.lens; overlap=false, ctx=ctx)
+    Float64.(u), Float64.(ub)
+end
+
 # ---- consumers of the code records (SURVEY.md §8f-4; _2_enumerate.jl) --------------------------------------------------------
 codes_mag_histogram!(hist::DeviceBuffer, ctx::Context, recs::DeviceBuffer, n::Integer) =      # 65536 UInt32 bins over the Float16 magnitudes
     check(ccall((:motifs_codes_mag_histogram_dev, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}), ctx.h, recs.p, n, hist.p))

@@ -17,6 +17,7 @@ ABI_VERSION = 3
 COMM_ID_BYTES = 128
 DATA_CODES_U8, DATA_ONEHOT_F32, DATA_ONEHOT_F16 = 0, 1, 2
 KS_ENCODE, KS_SCAN_DENSE, KS_SCAN_COUNT, KS_SCAN_OFFSETS, KS_SCAN_FILL, KS_TRAIN_STEP, KS_TRAIN_ISTA_BWD = range(7)
+KS_OCC_RECORDS, KS_OCC_ROWS, KS_OCC_OVERLAP = 7, 8, 9
 SCAN_BATCH = 5000
 SCAN_MAX_LEN = 64
 
@@ -124,6 +125,7 @@ SIGNATURES = {
     "motifs_hits_threshold_counts_dev": (_int, [_p, _p, _p, _i64, _int, _p, _int, _p]),
     "motifs_hits_filter_dev": (_int, [_p, _p, _p, _i64, _int, _p, _p, _p, C.POINTER(_i64)]),
     "motifs_hits_count_matrices_dev": (_int, [_p, _p, _i64, _p, _int, _i64, _p, _int, _int, _int, _p]),
+    "motifs_hits_occupancy_dev": (_int, [_p, _p, _i64, _p, _i64, _i64, _i64, _int, _p, _int, _p, _int, _p, _p, _p]),
     "motifs_codes_mag_histogram_dev": (_int, [_p, _p, _i64, _p]),
     "motifs_codes_filter_dev": (_int, [_p, _p, _i64, C.c_double, _p, C.POINTER(_i64)]),
     "motifs_triplets_offsets_dev": (_int, [_p, _p, _i64, _p, C.POINTER(_i64)]),
@@ -340,6 +342,15 @@ class Context:
         lens = np.ascontiguousarray(lens, dtype=np.int64)
         check(lib().motifs_hits_count_matrices_dev(self._h, _p(hits_ptr), int(n), _p(codes_ptr), int(L), int(n0), _np_ptr(lens), int(K),
                                                    int(maxlen), int(bool(comp)), _p(counts_ptr)))
+
+    def hits_occupancy_dev(self, hits_a_ptr, n_a, hits_b_ptr, n_b, n0, N, L, lens, motif_map, K_out, occupied_ptr, uniq_ptr=None,
+                           overlap_ptr=None):
+        """motifs_hits_occupancy_dev: lens (K_in,) int64 by m; motif_map (K_in,) int32 or None (identity).  Adds to the outputs."""
+        lens = np.ascontiguousarray(lens, dtype=np.int64)
+        mm = None if motif_map is None else np.ascontiguousarray(motif_map, dtype=np.int32)
+        check(lib().motifs_hits_occupancy_dev(self._h, _p(hits_a_ptr or None), int(n_a), _p(hits_b_ptr or None), int(n_b), int(n0), int(N),
+                                              int(L), _np_ptr(lens), len(lens), _np_ptr(mm), int(K_out), _p(occupied_ptr), _p(uniq_ptr or None),
+                                              _p(overlap_ptr or None)))
 
     # ---- consumers of the code records (SURVEY §8f-4) ----
     def codes_mag_histogram_dev(self, recs_ptr, n, hist_ptr):

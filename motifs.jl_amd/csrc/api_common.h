@@ -60,6 +60,9 @@ enum KernelSlot {
     KS_SCAN_FILL = 4,
     KS_TRAIN_STEP = 5,
     KS_TRAIN_ISTA_BWD = 6,
+    KS_OCC_RECORDS = 7,
+    KS_OCC_ROWS = 8,
+    KS_OCC_OVERLAP = 9,
     KS_COUNT_
 };
 
@@ -91,6 +94,7 @@ struct motifs_ctx {
     motifs::DevBuf cnt2, centries2; // the reverse strand's cells / entries when one candidate launch serves both strands of gpu_scan
     motifs::DevBuf cm_lens;         // motifs_hits_count_matrices_dev: the PWM lengths of the last call (uploaded again only when they change)
     std::vector<int32_t> cm_lens_host;
+    motifs::DevBuf occ_ws, occ_small, occ_pairs;   // motifs_hits_occupancy_dev: one chunk's row keys + bitmaps, the motif table, the pair sums
     int cg_chunks = -1;             // chunk groups of the re-scoring (scan_mfma.hip): -1 = when the table does not fit the LDS; MOTIFS_CG_CHUNKS overrides
     bool dense_fused = true;        // a17's tensor in one kernel (scan_dense.hip) where the bank fits it; candidate kernel + stage_hits<.., 2> otherwise
     int32_t scan_plan[4] = {0, 0, 0, 0};   // motifs_ctx_scan_plan

@@ -191,3 +191,137 @@ def enumerate_triplets(ctx, recs_t, n, h):
     v = vals[perm].cpu().numpy().view(_lib.TRIPLET_VAL_DTYPE)
     return {"keys": kk, "counts": cnt, "offsets": np.concatenate([[0], np.cumsum(cnt)]), "values": v, "n_triplets": int(total),
             "ranges": (starts, lens)}
+
+
+# ---- site occupancy and motif overlap (src/inference/_h4_overlap_ratio.jl, _h7_fisher.jl, _h8_remove_redundancy.jl:73-104) --------------
+def occupancy(ctx, strands, lens, N, L, n0=0, motif_map=None, K_out=None, overlap=True, reducer=None):
+    """get_union_ranges + total_active_position, the get_uniq_pos counts and get_overlap_ratio's pair sums of the device record
+    arrays `strands` = [(hits_t, n_records, ...), ...] (at most two: forward and reverse, pooled per read as ms.positions pools
+    them) over reads n0+1 .. n0+N of length L, in one library call (motifs_hits_occupancy_dev).  motif_map (K_in,): the output
+    row of every motif, -1 = leave it out (a length window of merge_to_remove_redundancy!).  reducer (parallel.make_reducer):
+    the three sums are summed over the ranks' shards on the device before they come back.
+    Returns (occupied (K_out,), uniq (K_out,), overlap (K_out, K_out) or None) as int64; overlap's diagonal is occupied."""
+    torch = _torch()
+    lens = np.ascontiguousarray(lens, dtype=np.int64)
+    if motif_map is not None:
+        motif_map = np.ascontiguousarray(motif_map, dtype=np.int32)
+        K_out = int(motif_map.max()) + 1 if K_out is None else int(K_out)
+    elif K_out is None:
+        K_out = len(lens)
+    strands = [(s[0], int(s[1])) for s in strands]
+    if len(strands) > 2:
+        raise ValueError("occupancy takes the records of at most two arrays (forward, reverse)")
+    dev = next((h.device for h, _ in strands if h is not None), torch.device("cuda", ctx.device))
+    while len(strands) < 2:
+        strands.append((None, 0))
+    occ = torch.zeros(K_out, dtype=torch.int64, device=dev)
+    uq = torch.zeros(K_out, dtype=torch.int64, device=dev)
+    ov = torch.zeros((K_out, K_out), dtype=torch.int64, device=dev) if overlap else None
+    _torch_first(occ)
+    (ha, na), (hb, nb) = strands
+    ctx.hits_occupancy_dev(ha.data_ptr() if na else None, na, hb.data_ptr() if nb else None, nb, n0, N, L, lens, motif_map, K_out,
+                           occ.data_ptr(), uq.data_ptr(), ov.data_ptr() if overlap else None)
+    if reducer is not None:
+        for t in (occ, uq) + ((ov,) if overlap else ()):
+            reducer.sum_i64_(t)
+    return occ.cpu().numpy(), uq.cpu().numpy(), (ov.cpu().numpy() if overlap else None)
+
+
+def overlap_ratio(occupied, overlap):
+    """get_overlap_ratio's matrix (_h4:86-117) from the exact sums: o = Float32(overlap), ratio = o / (Float32(a_i + a_j) - o) in
+    Float32 (Julia's promotion of Int - Float32), zero diagonal (the matrix starts as zeros), NaN where both motifs cover nothing."""
+    a = np.asarray(occupied, dtype=np.int64)
+    o = np.asarray(overlap, dtype=np.int64).astype(np.float32)
+    den = (a[:, None] + a[None, :]).astype(np.float32) - o
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = (o / den).astype(np.float32)
+    np.fill_diagonal(r, np.float32(0))
+    return r
+
+
+def connected_components(olap, thresh=0.8):
+    """return_connected_components (_h8:73-104): breadth-first trees of `olap .> thresh`, discovered in the same order (FIFO queue,
+    neighbours in ascending index).  0-based motif indices."""
+    from collections import deque
+
+    A = np.asarray(olap) > thresh
+    n = A.shape[0]
+    marked = np.zeros(n, dtype=bool)
+    trees = []
+    for i in range(n):
+        if marked[i]:
+            continue
+        marked[i] = True
+        sub, q = [i], deque([i])
+        while q:
+            v = q.popleft()
+            for j in np.nonzero(A[v])[0]:
+                if not marked[j]:
+                    marked[j] = True
+                    sub.append(int(j))
+                    q.append(int(j))
+        trees.append(sub)
+    return trees
+
+
+def fisher_pvec(a, b, N, L):
+    """fisher_pvec (_h7:21-36): right tail of Fisher's exact test on [[a, N L - a], [b, N L - b]] per motif, 1.0 where a = b = 0.
+    (test=true passes N_test as N.)"""
+    from scipy.stats import fisher_exact
+
+    total = int(N) * int(L)
+    out = np.ones(len(a), dtype=np.float64)
+    for i, (ai, bi) in enumerate(zip(a, b)):
+        ai, bi = int(ai), int(bi)
+        if ai == 0 and bi == 0:
+            continue
+        out[i] = fisher_exact([[ai, total - ai], [bi, total - bi]], alternative="greater")[1]
+    return out
+
+
+def _dict_records(positions, lens):
+    """ms.positions-style dictionaries -> one record array on the device (pooled: the dictionaries already pool both strands),
+    with the read count and the shortest L that holds every window."""
+    torch = _torch()
+    m, n, l = [], [], []
+    for i, d in enumerate(positions or []):
+        for key, ls in d.items():
+            m.extend([i + 1] * len(ls))
+            n.extend([int(key)] * len(ls))
+            l.extend(int(x) for x in ls)
+    rec = np.stack([np.asarray(m, np.int64), np.asarray(n, np.int64), np.asarray(l, np.int64)], axis=1) if m else np.zeros((0, 3), np.int64)
+    lens = np.asarray(lens, dtype=np.int64)
+    N = int(rec[:, 1].max()) if len(rec) else 0
+    L = int((rec[:, 2] + lens[rec[:, 0] - 1] - 1).max()) if len(rec) else 1
+    t = torch.from_numpy(rec.astype(np.uint32).view(np.int32)).cuda() if len(rec) else None
+    return t, len(rec), N, L
+
+
+def _dict_occupancy(ctx, positions, lens, overlap, L=None, N=None):
+    t, n, N_, L_ = _dict_records(positions, lens)
+    from . import scan
+
+    ctx = ctx or scan.default_context()
+    return occupancy(ctx, [(t, n)], lens, max(N or 0, N_), max(L or 1, L_), overlap=overlap)
+
+
+def get_overlap_ratio(ms, L, ctx=None):
+    """get_overlap_ratio(ms) (_h4:86-117) on the dictionaries of a scan.Motifs: (num_motifs, num_motifs) Float32."""
+    occ, _, ov = _dict_occupancy(ctx, ms.positions, ms.lens, True, L=L)
+    return overlap_ratio(occ, ov)
+
+
+def get_fisher_p_values(ms, data, test=False, ctx=None):
+    """get_fisher_p_values (_h7:38-44): occupied positions of ms.positions and ms.positions_bg, then fisher_pvec with N (N_test when
+    test) x L of `data` (a scan.FastaData)."""
+    occ, _, _ = _dict_occupancy(ctx, ms.positions, ms.lens, False, L=data.L)
+    occ_bg, _, _ = _dict_occupancy(ctx, ms.positions_bg, ms.lens, False, L=data.L)
+    N = data.data_matrix_test.reshape(data.data_matrix_test.shape[0], -1).shape[0] if test else data.N
+    return fisher_pvec(occ, occ_bg, N, data.L)
+
+
+def get_uniq_counts(ms, ctx=None):
+    """get_uniq_counts (_h4:13-15): unique starts per motif over the reads, of ms.positions and ms.positions_bg (Float64)."""
+    _, uq, _ = _dict_occupancy(ctx, ms.positions, ms.lens, False)
+    _, uq_bg, _ = _dict_occupancy(ctx, ms.positions_bg, ms.lens, False)
+    return uq.astype(np.float64), uq_bg.astype(np.float64)
